@@ -106,6 +106,45 @@ def attach_traffic(out, workload, dom, default_config):
         out['roofline']['traffic_unit'] = 'bytes/launch (PMC pass: %s)' % src
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: writes every tensor of ``arrays`` ({name: tensor}) as out_dir/<name>.npy, float64 as float64 and everything
+    else as float32 (the integer outputs -- ids, lengths -- are far below 2**24, so exact), for comparing two builds output for output.
+    At most ``limit`` bytes in all: taken from the smallest to the largest, an array larger than an equal share of the bytes still
+    free is written as a fixed sample of its elements instead, the 1-D array flat[np.sort(default_rng(seed).choice(n, k, replace=False))]
+    -- the same elements in every run of the same shape.  Returns {name: (shape, elements written)}."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((name, t.detach(), 8 if t.dtype == torch.float64 else 4) for name, t in arrays.items()),
+                   key=lambda it: it[1].numel() * it[2])
+    free = limit - 256 * len(items)                       # the .npy headers (128 bytes for these shapes)
+    written = {}
+    for i, (name, t, size) in enumerate(items):
+        n, share = t.numel(), free // (len(items) - i)
+        flat = t.reshape(-1)
+        if n * size > share:
+            idx = np.sort(np.random.default_rng(seed).choice(n, share // size, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if size == 8 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a.reshape(t.shape) if a.size == n else a)
+        free -= a.nbytes
+        written[name] = (tuple(t.shape), a.size)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + '.npy')) for name in written)
+    assert total <= limit, (total, limit)
+    for name, (shape, k) in written.items():
+        n = int(np.prod(shape))
+        print('bench.py: --dump-outputs %s/%s.npy: %s%s' % (out_dir, name, shape, '' if k == n else ', sample of %d of %d elements' % (k, n)),
+              file=sys.stderr)
+    return written
+
+
+def decoded_ids(ids, lens):
+    """greedy-decode ids [B][T] with -1 behind each row's decoded length (the buffer's tail is not part of the result)"""
+    cols = torch.arange(ids.shape[1], device=ids.device)
+    return torch.where(cols[None, :] < lens[:, None], ids, torch.full_like(ids, -1))
+
+
 def cpu_baseline(variant, t_pad, vocab, batch=32, seconds=10.0, budget_s=30.0):
     """CPU restatement ("port": oracle/torch_ref.py on torch-CPU ops + the numpy fbank oracle) of the identical step at the
     SAME batch the GPU number is quoted on, timed on this host's cores on a bounded sample: one untimed warm-up
@@ -219,6 +258,12 @@ def run_am_lm(args):
         dist.barrier()
     dt = time.perf_counter() - t0
     timed = ops.TIMER.summary(); ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            'am_logits': am.logits, 'am_loss': am.loss, 'am_decoded_ids': decoded_ids(am.dec_ids, am.dec_len), 'am_decoded_len': am.dec_len,
+            'am_edit_distance': am.dist, 'lm_logits': lm.logits[..., :lm.V], 'lm_loss': lm.loss,
+            'lm_decoded_ids': decoded_ids(lm.dec_ids, lm.dec_len), 'lm_decoded_len': lm.dec_len,
+            'am_params': am.theta, 'am_grad': am.grad, 'lm_params': lm.theta, 'lm_grad': lm.grad})
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device='cuda'); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
     if rank == 0:
@@ -293,6 +338,9 @@ def run_lm(args):
         dist.barrier()
     dt = time.perf_counter() - t0
     timed = ops.TIMER.summary(); ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'logits': eng.logits[:, :eng.V], 'loss': eng.loss_rows, 'predictions': eng.preds,
+                                         'params': eng.theta, 'grad': eng.grad})
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device='cuda'); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
     if rank == 0:
@@ -386,6 +434,11 @@ def run_transformer(args):
         dist.barrier()
     dt = time.perf_counter() - t0
     timed = ops.TIMER.summary(); ops.TIMER = None
+    if args.dump_outputs and rank == 0:
+        outs = {'logits': eng.logits[:, :eng.V], 'loss': eng.loss_rows, 'predictions': eng.preds, 'params': eng.theta, 'grad': eng.grad}
+        if prenet:
+            outs.update(prenet_params=pre.theta, prenet_grad=pre.grad)
+        dump_outputs(args.dump_outputs, outs)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device='cuda'); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
     if rank == 0:
@@ -567,10 +620,10 @@ def prime_gpu(steps):
         if skip:
             skip = False
             continue
-        if a in ('--gpus', '--steps', '--warmup', '--prime-steps'):
+        if a in ('--gpus', '--steps', '--warmup', '--prime-steps', '--dump-outputs'):
             skip = True
             continue
-        if a.split('=')[0] in ('--gpus', '--steps', '--warmup', '--prime-steps') or a in ('--kernel-table', '--no-cpu-baseline'):
+        if a.split('=')[0] in ('--gpus', '--steps', '--warmup', '--prime-steps', '--dump-outputs') or a in ('--kernel-table', '--no-cpu-baseline'):
             continue
         argv.append(a)
     cmd = [sys.executable, os.path.abspath(__file__)] + argv + ['--gpus', '1', '--steps', str(steps), '--warmup', '3',
@@ -670,7 +723,12 @@ def main():
     ap.add_argument('--prime-steps', type=int, default=0,
                     help='untimed steps of the same workload in a child process before this one touches the GPU (default 0: none; '
                          'never with more than one rank); see prime_gpu()')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy, float32 / float64, at most '
+                         '64 MB in all (a fixed sample of the larger arrays); see dump_outputs()')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1 (the timed steps)')
     if args.scaling == 'strong' and (args.gpus < 1 or args.batch % args.gpus != 0):
         print('bench.py: --scaling strong splits the global batch %d over %d GPUs: the GPU count must divide it' % (args.batch, args.gpus), file=sys.stderr)
         return 2
@@ -912,6 +970,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     mean_loss, label_err = (0.0, 0.0) if args.inference else eng.fetch_scalars()
+    if args.dump_outputs and rank == 0:
+        # before the roofline pass below: its extra steps go on training
+        outs = {'logits': eng.logits, 'decoded_ids': decoded_ids(eng.dec_ids, eng.dec_len), 'decoded_len': eng.dec_len}
+        if args.inference:
+            outs['neg_sum_logits'] = eng.neg_sum
+        else:
+            outs.update(loss=eng.loss, edit_distance=eng.dist, params=eng.theta, grad=eng.grad)
+        dump_outputs(args.dump_outputs, outs)
 
     # Roofline pass (after the timed region, never part of `value`): when the dominant kernel overlaps with others in the real
     # step, its launch duration is measured in min(K, 5) single-stream steps of the same workload.

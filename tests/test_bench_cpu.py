@@ -40,7 +40,7 @@ def test_prime_child_gets_the_workload_but_not_the_timing_flags(monkeypatch):
 
     monkeypatch.setattr(subprocess, 'run', fake_run)
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '8', '--steps', '20', '--warmup=5', '--workload', 'se_dfcnn', '--tpad', '1000',
-                                      '--kernel-table', '--prime-steps', '40'])
+                                      '--kernel-table', '--prime-steps', '40', '--dump-outputs', 'dumps'])
     monkeypatch.setenv('RANK', '3'); monkeypatch.setenv('LOCAL_RANK', '3'); monkeypatch.setenv('WORLD_SIZE', '8')
     monkeypatch.setenv('MASTER_ADDR', '127.0.0.1'); monkeypatch.setenv('MASTER_PORT', '29500')
     assert bench.prime_gpu(40) == 6.7
@@ -48,7 +48,7 @@ def test_prime_child_gets_the_workload_but_not_the_timing_flags(monkeypatch):
     tail = cmd[2:]
     assert tail[:4] == ['--workload', 'se_dfcnn', '--tpad', '1000']                 # the workload travels
     assert tail[4:] == ['--gpus', '1', '--steps', '40', '--warmup', '3', '--prime-steps', '0', '--no-cpu-baseline']
-    assert '--kernel-table' not in tail and '--warmup=5' not in tail
+    assert '--kernel-table' not in tail and '--warmup=5' not in tail and 'dumps' not in tail          # the parent writes the dump
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):    # the child is a single process on the rank's GPU
         assert k not in env
     assert env['ASR_BENCH_DEVICE'] == '3'
@@ -173,3 +173,37 @@ def test_stream_calibration_keeps_two_streams_unless_one_wins_clearly():
     assert bench.keep_two_streams(6.115, 6.44) and bench.keep_two_streams(4.181, 4.325)
     assert bench.keep_two_streams(4.387, 4.335) and bench.keep_two_streams(6.911, 6.829)
     assert not bench.keep_two_streams(7.2, 6.7) and not bench.keep_two_streams(7.3, 6.75)
+
+
+def test_steps_must_be_at_least_one(monkeypatch):
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb_and_samples_the_same_elements_every_time(tmp_path):
+    import numpy as np
+    import torch
+    n = 12 << 20                                              # 48 MB each: together over the limit; values = flat index, exact in float32
+    arrays = {'a': torch.arange(n, dtype=torch.float32), 'b': torch.arange(n, dtype=torch.int32).reshape(3, -1),
+              'ids': torch.tensor([[3, 1, -1]], dtype=torch.int32), 'f64': torch.linspace(0, 1, 5, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / 'x'), arrays)
+    files = sorted(os.listdir(tmp_path / 'x'))
+    assert files == ['a.npy', 'b.npy', 'f64.npy', 'ids.npy']
+    assert 60 << 20 < sum(os.path.getsize(tmp_path / 'x' / f) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / 'x' / f) for f in files}
+    assert got['ids'].dtype == np.float32 and got['ids'].tolist() == [[3, 1, -1]]
+    assert got['f64'].dtype == np.float64 and np.array_equal(got['f64'], arrays['f64'].numpy())
+    for k in ('a', 'b'):                                      # a sorted sample of distinct elements, listed by flat index
+        assert got[k].dtype == np.float32 and got[k].ndim == 1 and 7 << 20 < got[k].size < n
+        assert np.all(np.diff(got[k]) > 0) and got[k][-1] < n
+    bench.dump_outputs(str(tmp_path / 'y'), arrays)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'y' / f), got[f[:-4]])
+
+
+def test_decoded_ids_hide_the_buffer_tail():
+    import torch
+    ids = torch.tensor([[5, 6, 7], [8, 9, 1], [2, 2, 2]], dtype=torch.int32)
+    assert bench.decoded_ids(ids, torch.tensor([2, 0, 3], dtype=torch.int32)).tolist() == [[5, 6, -1], [-1, -1, -1], [2, 2, 2]]

@@ -71,3 +71,23 @@ def test_strong_scaling_splits_the_global_batch_and_reproduces_the_one_rank_grad
 def test_strong_scaling_refuses_a_rank_count_that_does_not_divide_the_batch():
     p, lines = _run_bench(['--gpus', '3', '--batch', '32', '--scaling', 'strong'])
     assert p.returncode == 2 and not lines and 'must divide' in p.stderr.decode()
+
+
+def test_dump_outputs_is_the_last_timed_step_and_the_same_in_every_run(tmp_path):
+    """--dump-outputs: the outputs of the last timed step, in float32; the same arguments give the same inputs, so a second process writes
+    the same arrays, and the losses are the ones the JSON line reports."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        p, lines = _run_bench(['--batch', '2', '--dump-outputs', str(d)])
+        assert p.returncode == 0 and len(lines) == 1, p.stderr.decode(errors='replace')[-3000:]
+        runs.append((json.loads(lines[0]), {f[:-4]: np.load(d / f) for f in os.listdir(d)}))
+    (out, a), (_, b) = runs
+    assert sorted(a) == ['decoded_ids', 'decoded_len', 'edit_distance', 'grad', 'logits', 'loss', 'params']
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a['logits'].shape == (125, 2, 1536) and a['loss'].shape == (2,) and a['params'].shape == a['grad'].shape
+    assert np.array_equal((a['decoded_ids'] >= 0).sum(axis=1), a['decoded_len'])
+    assert abs(a['loss'].mean() - out['config']['mean_loss']) <= 1e-4 + 1e-5 * abs(out['config']['mean_loss'])
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
